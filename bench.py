@@ -12,9 +12,34 @@ one per-job throughput number BASELINE.md quotes for the reference
 (ResNet-18 bs16 = 57.68 steps/s = 922.9 samples/s on one V100).
 ``vs_baseline`` is per-GPU-normalized: (value / n_gpus) / 922.9.
 
+A plain run does only what that figure needs: set up, warm up, time
+``--steps`` steps, print one JSON result line.  ``--dump-outputs DIR``
+additionally writes what the last timed step computed (see below).
+
 Scheduler-level metrics (makespan + worst FTF rho on the 120-job trace,
-the reference's headline table) are produced by ``--trace-sim`` /
+the reference's headline table) take a CPU simulation of their own; they
+are produced only under ``--full`` (or ``--trace-sim``) /
 scripts/simulate.py and recorded in profiles/.
+
+``--dump-outputs DIR`` (rank 0) writes float32 ``DIR/<name>.npy`` files:
+  loss.npy     the loss the last timed step returned to its caller
+  params.npy   every model parameter after that step, flattened and
+               concatenated in ``named_parameters()`` order
+  buffers.npy  every floating-point model buffer (BatchNorm running
+               statistics), same layout
+Model initialisation and the data stream are seeded (``--seed``), so two
+runs with the same arguments see identical inputs.  A training step also
+reads the state the steps before it left, and that state does not repeat:
+MIOpen's backward-weight kernels accumulate in a run-dependent order, and
+SGD at lr 0.1 on random labels amplifies the rounding difference to O(1)
+within a few hundred steps.  So when (and only when) ``--dump-outputs``
+is given, the last timed step starts from the seeded initial state:
+parameters and buffers are copied back in place and the momentum buffers
+zeroed just before it (a few device copies, inside the timed loop; the
+captured graph stays valid).  Its batch is the one the data stream yields
+at that position.  What is written is then one whole step (forward,
+backward, fused optimizer) on inputs that are bit-identical across runs,
+and two builds can be compared element by element.
 
 Launch (multi-GPU, by the driver):
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
@@ -24,7 +49,9 @@ Launch (multi-GPU, by the driver):
 import argparse
 import json
 import os
+import shutil
 import sys
+import tempfile
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -45,6 +72,16 @@ def parse_args():
                    help="disable hipGraph capture of the train step")
     p.add_argument("--trace-sim", action="store_true",
                    help="also run the 120-job scheduler simulation (rank 0)")
+    p.add_argument("--full", action="store_true",
+                   help="also run every secondary measurement (today: the "
+                        "--trace-sim scheduler simulation); off by default "
+                        "so a plain run only times the training step")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last step's "
+                        "outputs (loss, parameters, buffers) as "
+                        "DIR/<name>.npy (float32, rank 0)")
+    p.add_argument("--seed", type=int, default=0,
+                   help="seed of the model initialisation")
     return p.parse_args()
 
 
@@ -53,6 +90,8 @@ def build_flagship(args, device):
     from shockwave_amd.ops.optim import FusedSGD
     from shockwave_amd.parallel import BucketedDataParallel
 
+    # seeded init: the same arguments give the same weights every run
+    torch.manual_seed(args.seed)
     model = resnet18_cifar().to(device)
     if device.type == "cuda":
         # NHWC keeps MIOpen on its native igemm path (no per-conv
@@ -65,6 +104,49 @@ def build_flagship(args, device):
     opt = FusedSGD(model.parameters(), lr=0.1, momentum=0.9, weight_decay=5e-4)
     criterion = torch.nn.CrossEntropyLoss().to(device)
     return model, opt, criterion
+
+
+def dump_outputs(out_dir, model, loss):
+    """Write what the last timed step computed as float32 .npy files."""
+    import numpy as np
+
+    def flat(tensors):
+        parts = [t.detach().float().reshape(-1).cpu() for t in tensors]
+        if not parts:
+            return np.zeros(0, dtype=np.float32)
+        return torch.cat(parts).numpy()
+
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"),
+            loss.detach().float().reshape(-1).cpu().numpy())
+    np.save(os.path.join(out_dir, "params.npy"),
+            flat(p for _, p in model.named_parameters()))
+    np.save(os.path.join(out_dir, "buffers.npy"),
+            flat(b for _, b in model.named_buffers()
+                 if b.is_floating_point()))
+
+
+class SeededState:
+    """Snapshot of model parameters and buffers, restorable in place."""
+
+    def __init__(self, model, opt):
+        self.opt = opt
+        self.live = [t.detach() for t in model.parameters()]
+        self.live += [t.detach() for t in model.buffers()]
+        self.saved = [t.clone() for t in self.live]
+
+    @torch.no_grad()
+    def restore(self):
+        fp = [i for i, t in enumerate(self.live) if t.is_floating_point()]
+        torch._foreach_copy_([self.live[i] for i in fp],
+                             [self.saved[i] for i in fp])
+        for i, t in enumerate(self.live):
+            if not t.is_floating_point():
+                t.copy_(self.saved[i])
+        bufs = [s["momentum_buffer"] for s in self.opt.state.values()
+                if "momentum_buffer" in s]
+        if bufs:
+            torch._foreach_zero_(bufs)
 
 
 def main():
@@ -96,6 +178,7 @@ def main():
             )
 
     model, opt, criterion = build_flagship(args, device)
+    seeded = SeededState(model, opt) if args.dump_outputs else None
     from shockwave_amd.runtime.lease_iterator import LeaseIterator, NullLeaseClient
     from shockwave_amd.workloads import common
     from shockwave_amd.data.synthetic import SyntheticImages
@@ -105,7 +188,9 @@ def main():
     dataset = SyntheticImages(50000, image_size=32, num_classes=10, seed=rank)
     loader = DataLoader(dataset, batch_size=bs, shuffle=False, num_workers=0,
                         drop_last=True, pin_memory=use_cuda)
-    ckpt_dir = os.path.join("/tmp", f"swq_bench_{rank}")
+    # private scratch directory for the iterator's round log (a fixed
+    # name under the shared temp dir can belong to another user)
+    ckpt_dir = tempfile.mkdtemp(prefix=f"swq_bench_{rank}_")
     lease_it = LeaseIterator(
         loader, ckpt_dir, lambda: None, lambda s: None,
         synthetic_data=False, write_on_close=False, client=NullLeaseClient(),
@@ -169,6 +254,7 @@ def main():
                 common.zero_grads(model)
                 loss = criterion(model(x), y)
                 loss.backward()
+                return loss
 
             partial = try_graph_step(fwd_bwd, [static_x, static_y])
             if partial is not None:
@@ -181,13 +267,14 @@ def main():
             x = x.to(memory_format=torch.channels_last)
         y = y.to(device, non_blocking=True)
         if graphed is not None:
-            graphed(x, y)
+            return graphed(x, y)
         elif partial is not None:
-            partial(x, y)
+            loss = partial(x, y)
             model.finish_gradient_sync()
             opt.step()
+            return loss
         else:
-            compute_step(x, y)
+            return compute_step(x, y)
 
     def barrier_sync():
         if distributed:
@@ -203,10 +290,16 @@ def main():
 
     barrier_sync()
     t0 = time.time()
-    for _ in range(args.steps):
-        train_step()
+    last_loss = None
+    for i in range(args.steps):
+        if seeded is not None and i == args.steps - 1:
+            seeded.restore()
+        last_loss = train_step()
     barrier_sync()
     elapsed = time.time() - t0
+
+    if args.dump_outputs and rank == 0 and last_loss is not None:
+        dump_outputs(args.dump_outputs, model, last_loss)
 
     # MAX over ranks
     if distributed:
@@ -252,13 +345,14 @@ def main():
         },
     }
 
-    if args.trace_sim and rank == 0:
-        sys.path.insert(0, os.path.join(os.path.dirname(__file__), "scripts"))
+    if (args.full or args.trace_sim) and rank == 0:
+        repo = os.path.dirname(os.path.abspath(__file__))
+        sys.path.insert(0, os.path.join(repo, "scripts"))
         from simulate import run_simulation
 
         sim = run_simulation(
-            "traces/tacc_like_120.trace",
-            "traces/mi355x_throughputs.json",
+            os.path.join(repo, "traces", "tacc_like_120.trace"),
+            os.path.join(repo, "traces", "mi355x_throughputs.json"),
             "shockwave",
             num_gpus=32,
         )
@@ -272,6 +366,9 @@ def main():
         import torch.distributed as dist
 
         dist.destroy_process_group()
+
+    lease_it.close()
+    shutil.rmtree(ckpt_dir, ignore_errors=True)
 
 
 if __name__ == "__main__":

@@ -37,9 +37,13 @@ class CheckpointStore:
     def __init__(
         self,
         job_checkpoint_dir: str,
-        shm_root: str = "/dev/shm/swq_ckpt",
+        shm_root: Optional[str] = None,
         shared_dir: Optional[str] = None,
     ):
+        # SWQ_SHM_ROOT moves the RAM tier (e.g. to a per-user directory on
+        # a node where /dev/shm/swq_ckpt belongs to someone else)
+        if shm_root is None:
+            shm_root = os.environ.get("SWQ_SHM_ROOT", "/dev/shm/swq_ckpt")
         self.dir = job_checkpoint_dir
         # key the RAM tier by the full durable path so distinct checkpoint
         # dirs (and re-created temp dirs) never share shm state

@@ -210,26 +210,27 @@ class TestFusedAdamStateDict:
 class TestBsPatternOracleParity:
     """The adaptation twins' bs schedules must equal the reference's
     oracle tables exactly, including its loop-ordering quirk (check-first
-    segments leave the final epoch at base bs).  Skips without the
-    reference tree; patterns are data regenerated by
-    scripts/gen_bs_ladder.py."""
-
-    REF = "/root/reference/scheduler/utils.py"
+    segments leave the final epoch at base bs).  Our patterns are data
+    regenerated by scripts/gen_bs_ladder.py; the reference oracle's
+    outputs are recorded in tests/golden/reference/bs_patterns.json by
+    scripts/gen_reference_golden.py."""
 
     def _load(self, name):
-        import ast
-
-        import pytest as _pytest
-
+        import json
         import os
-        if not os.path.exists(self.REF):
-            _pytest.skip("reference tree not present")
-        ns = {}
-        for node in ast.parse(open(self.REF).read()).body:
-            if isinstance(node, ast.FunctionDef) and node.name == name:
-                exec(compile(ast.Module(body=[node], type_ignores=[]),
-                             self.REF, "exec"), ns)
-        return ns[name]
+
+        path = os.path.join(os.path.dirname(__file__), "golden",
+                            "reference", "bs_patterns.json")
+        with open(path) as f:
+            table = json.load(f)[name]
+        # stored run-length encoded: [[batch size, epochs], ...]
+        return {
+            key: {
+                E: [bs for bs, n in runs for _ in range(n)]
+                for E, runs in by_epochs.items()
+            }
+            for key, by_epochs in table.items()
+        }
 
     def test_gns_ladder_matches_reference(self):
         import json
@@ -237,22 +238,24 @@ class TestBsPatternOracleParity:
 
         from shockwave_amd.core import bs_patterns as bp
 
-        ref = self._load("get_gns_bs_pattern")
+        ref = self._load("gns")
         keys = json.load(open(os.path.join(
             os.path.dirname(bp.__file__), "data", "gns_bs_ladder.json"
         ))).keys()
+        assert set(keys) == set(ref)
         for key in keys:
             model, bs, sf = key.split("|")
             jt = f"{model} (batch size {bs})"
             for E in (1, 5, 12, 31, 59, 100, 200, 400):
-                r = [int(x) for x in ref(jt, int(bs), E, int(sf))]
+                r = ref[key][str(E)]
+                assert len(r) == E
                 o = bp.gns_bs_pattern(jt, int(bs), E, int(sf))
                 assert r == o, (key, E)
 
     def test_accordion_matches_reference(self):
         from shockwave_amd.core.bs_patterns import accordion_bs_pattern
 
-        ref = self._load("get_accordion_bs_pattern")
+        ref = self._load("accordion")
         combos = (
             [("ResNet-18", b) for b in (16, 32, 64, 128, 256)]
             + [("ResNet-50", b) for b in (16, 32, 64)]
@@ -263,5 +266,6 @@ class TestBsPatternOracleParity:
         for model, bs in combos:
             jt = f"{model} (batch size {bs})"
             for E in (1, 10, 31, 100, 270):
-                r = [int(x) for x in ref(jt, bs, E, 1)]
+                r = ref[f"{model}|{bs}"][str(E)]
+                assert len(r) == E
                 assert r == accordion_bs_pattern(jt, bs, E), (jt, E)

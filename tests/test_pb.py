@@ -5,9 +5,10 @@ google.protobuf runtime, so rpc/pb.py parses the committed .proto files
 and materializes real message classes at runtime.  These tests prove
 (1) the classes round-trip, (2) their bytes interoperate with classes
 built from the REFERENCE's own .proto files (the actual wire-compat
-claim), and (3) the full RPC stack works with SWQ_RPC_CODEC=proto.
+claim; the reference side is recorded under tests/golden/reference/), and (3) the full RPC stack works with SWQ_RPC_CODEC=proto.
 """
 
+import json
 import os
 import sys
 
@@ -16,9 +17,9 @@ import pytest
 REPO = os.path.join(os.path.dirname(__file__), "..")
 sys.path.insert(0, REPO)
 
-REF_PROTOS = "/root/reference/scheduler/runtime/protobuf"
+GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "reference")
 
-from shockwave_amd.rpc.pb import Schema, our_schema  # noqa: E402
+from shockwave_amd.rpc.pb import our_schema  # noqa: E402
 
 
 class TestRuntimeStubs:
@@ -67,35 +68,47 @@ class TestRuntimeStubs:
         assert s.to_dict(m2)["data"] == b"\x00\x01\xff"
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_PROTOS),
-                    reason="reference protos absent")
 class TestReferenceWireCompat:
     """Bytes serialized by classes built from the REFERENCE's .proto
     files parse into ours with identical content, and vice versa — the
-    wire format, not just the schema text, is compatible."""
+    wire format, not just the schema text, is compatible.  The
+    reference's bytes and schema facts are recorded under
+    tests/golden/reference/ (scripts/gen_reference_golden.py)."""
 
     @pytest.fixture(scope="class")
-    def ref(self):
-        return Schema(REF_PROTOS, "reference")
+    def wire(self):
+        with open(os.path.join(GOLDEN, "wire_messages.json")) as f:
+            return json.load(f)
 
-    def test_done_request_ours_to_reference(self, ref):
+    @pytest.fixture(scope="class")
+    def ref_fields(self):
+        with open(os.path.join(GOLDEN, "proto_fields.json")) as f:
+            return json.load(f)
+
+    def test_done_request_ours_to_reference(self, wire):
         s = our_schema()
-        b = s.to_message("DoneRequest", {
+        payload = {
             "worker_id": 3, "job_id": [1, 2], "num_steps": [10, 20],
             "execution_time": [1.5, 2.5], "iterator_log": ["a", "b"],
-        }).SerializeToString()
-        m = ref.messages["DoneRequest"]()
-        m.ParseFromString(b)
-        d = ref.to_dict(m)
+        }
+        rec = wire["DoneRequest"]
+        assert rec["payload"] == payload
+        b = s.to_message("DoneRequest", payload).SerializeToString()
+        # byte-identical to what the reference's classes serialize, so
+        # the reference parses ours exactly as it parses its own
+        assert b == bytes.fromhex(rec["hex"])
+        d = rec["decoded"]
         assert d["job_id"] == [1, 2]
         assert d["execution_time"] == [1.5, 2.5]
         assert d["iterator_log"] == ["a", "b"]
 
-    def test_lease_response_reference_to_ours(self, ref):
-        b = ref.to_message("UpdateLeaseResponse", {
+    def test_lease_response_reference_to_ours(self, wire):
+        rec = wire["UpdateLeaseResponse"]
+        assert rec["payload"] == {
             "max_steps": 500, "max_duration": 120.5, "extra_time": 7.25,
             "run_time_so_far": 33, "deadline": 9000,
-        }).SerializeToString()
+        }
+        b = bytes.fromhex(rec["hex"])
         s = our_schema()
         m = s.messages["UpdateLeaseResponse"]()
         m.ParseFromString(b)
@@ -105,11 +118,13 @@ class TestReferenceWireCompat:
         assert d["extra_time"] == 7.25
         assert d["run_time_so_far"] == 33 and d["deadline"] == 9000
 
-    def test_heartbeat_nested_enum(self, ref):
-        b = ref.to_message("Heartbeat", {
+    def test_heartbeat_nested_enum(self, wire, ref_fields):
+        rec = wire["Heartbeat"]
+        assert rec["payload"] == {
             "worker_id": 7,
             "job_state": [{"job_id": 4, "status": 2}],
-        }).SerializeToString()
+        }
+        b = bytes.fromhex(rec["hex"])
         s = our_schema()
         m = s.messages["Heartbeat"]()
         m.ParseFromString(b)
@@ -118,13 +133,16 @@ class TestReferenceWireCompat:
         # enum numbering aligned with the reference's enums.proto
         assert s.enums["JobStatus"]["RUNNING"] == 2
         assert s.enums["JobStatus"]["SUCCEEDED"] == 3
+        assert ref_fields["enums"]["JobStatus"]["RUNNING"] == 2
+        assert ref_fields["enums"]["JobStatus"]["SUCCEEDED"] == 3
 
-    def test_every_shared_message_field_for_field(self, ref):
+    def test_every_shared_message_field_for_field(self, ref_fields):
         """Each message both schemas define carries the same
         (name, number, repeated) triples for the fields the REFERENCE
         declares (ours may extend into unused field space)."""
         s = our_schema()
-        shared = set(s.messages) & set(ref.messages)
+        ref_messages = ref_fields["messages"]
+        shared = set(s.messages) & set(ref_messages)
         assert len(shared) >= 13
         for name in shared:
             ours = {
@@ -132,8 +150,7 @@ class TestReferenceWireCompat:
                 for f in s.messages[name].DESCRIPTOR.fields
             }
             theirs = {
-                (f.name, f.number, f.is_repeated)
-                for f in ref.messages[name].DESCRIPTOR.fields
+                (fname, num, rep) for fname, num, rep in ref_messages[name]
             }
             assert theirs <= ours, (
                 f"{name}: reference fields {theirs - ours} missing here"

@@ -1,11 +1,13 @@
 """Compatibility with the reference's on-disk formats.
 
-These tests run only where the reference checkout is present (this build
-container); they prove a user can bring their existing Gavel/Shockwave
-traces to this framework unchanged.
+They prove a user can bring their existing Gavel/Shockwave traces to this
+framework unchanged.  The reference's data (its 120-job trace, V100
+oracle, solver settings, committed simulation results and protobuf field
+numbering) is recorded under tests/golden/reference/ by
+scripts/gen_reference_golden.py.
 """
 
-import glob
+import json
 import os
 
 import pytest
@@ -14,22 +16,15 @@ from shockwave_amd.core import trace as trace_mod
 from shockwave_amd.core.job_table import JobTable
 from shockwave_amd.core.job import Job
 
-REFERENCE = "/root/reference/scheduler"
+GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "reference")
 REPO = os.path.join(os.path.dirname(__file__), "..")
 
-needs_reference = pytest.mark.skipif(
-    not os.path.isdir(REFERENCE), reason="reference checkout not present"
-)
 
-
-@needs_reference
 class TestReferenceTraceCompat:
     def _trace(self):
-        paths = glob.glob(
-            os.path.join(REFERENCE, "traces", "reproduce", "120_*.trace")
-        )
-        assert paths
-        return paths[0]
+        path = os.path.join(GOLDEN, "trace_120.trace")
+        assert os.path.exists(path)
+        return path
 
     def test_parse_reference_trace(self):
         jobs, arrivals = trace_mod.parse_trace(self._trace())
@@ -101,48 +96,18 @@ class TestUpdateBsAllTemplates:
         assert str(old_bs * 2) in job.command
 
 
-@needs_reference
 class TestReferenceParity:
     """Run OUR simulator on the reference's own trace + V100 oracle and
-    compare against the result pickles the reference repo ships
-    (reproduce/pickles/tacc_32gpus) — profiles/REFERENCE_PARITY.md."""
+    compare against the results the reference repo ships
+    (reproduce/pickles/tacc_32gpus, recorded in sim_results.json) —
+    profiles/REFERENCE_PARITY.md."""
 
-    TRACE = os.path.join(
-        REFERENCE, "traces", "reproduce",
-        "120_0.2_5_100_40_25_0,0.5,0.5_0.6,0.3,0.09,0.01"
-        "_multigpu_dynamic.trace",
-    )
-    PICKLES = os.path.join(REFERENCE, "reproduce", "pickles", "tacc_32gpus")
+    TRACE = os.path.join(GOLDEN, "trace_120.trace")
 
     @staticmethod
     def _load_reference_pickle(policy):
-        import pickle
-
-        class _RefJobIdPair:
-            def __init__(self, *a, **k):
-                pass
-
-            def __hash__(self):
-                return hash((self.__dict__.get("_job0"),
-                             self.__dict__.get("_job1")))
-
-            def __eq__(self, o):
-                return (isinstance(o, _RefJobIdPair)
-                        and self.__dict__ == o.__dict__)
-
-        class RefUnpickler(pickle.Unpickler):
-            def find_class(self, module, name):
-                if module == "job_id_pair" and name == "JobIdPair":
-                    return _RefJobIdPair
-                return super().find_class(module, name)
-
-        path = os.path.join(
-            TestReferenceParity.PICKLES,
-            f"{policy}_120_0.2_5_100_40_25_0,0.5,0.5_0.6,0.3,0.09,0.01"
-            "_multigpu_dynamic_simulation.pickle",
-        )
-        with open(path, "rb") as f:
-            return RefUnpickler(f).load()
+        with open(os.path.join(GOLDEN, "sim_results.json")) as f:
+            return json.load(f)[policy]
 
     def _run_ours(self, policy, shockwave_config=None):
         import copy
@@ -152,7 +117,7 @@ class TestReferenceParity:
         from shockwave_amd.policies import get_policy
 
         tputs = read_throughputs(
-            os.path.join(REFERENCE, "tacc_throughputs.json")
+            os.path.join(GOLDEN, "tacc_throughputs.json")
         )
         jobs, arrivals = trace_mod.parse_trace(self.TRACE)
         profiles = [trace_mod.build_job_profile(j, tputs) for j in jobs]
@@ -189,10 +154,7 @@ class TestReferenceParity:
     def test_shockwave_matches_reference(self):
         """Independent EG MILP (scipy/HiGHS vs Gurobi): makespan and avg
         JCT within 5% of the reference's committed shockwave result."""
-        import json
-
-        cfg = json.load(open(os.path.join(
-            REFERENCE, "configurations", "tacc_32gpus.json")))
+        cfg = json.load(open(os.path.join(GOLDEN, "tacc_32gpus.json")))
         cfg["time_per_iteration"] = 120
         cfg["num_gpus"] = 32
         ref = self._load_reference_pickle("shockwave")
@@ -223,7 +185,6 @@ class TestProtoSchemaParity:
         os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
         "shockwave_amd", "rpc", "protos",
     )
-    REF_DIR = os.path.join(REFERENCE, "runtime", "protobuf")
 
     @staticmethod
     def _parse(path):
@@ -249,13 +210,15 @@ class TestProtoSchemaParity:
         return msgs
 
     def test_message_fields_match_reference(self):
-        if not os.path.isdir(self.REF_DIR):
-            pytest.skip("reference tree not present")
-        ours, ref = {}, {}
-        for d, out in ((self.OURS, ours), (self.REF_DIR, ref)):
-            for name in os.listdir(d):
-                if name.endswith(".proto"):
-                    out.update(self._parse(os.path.join(d, name)))
+        ours = {}
+        for name in os.listdir(self.OURS):
+            if name.endswith(".proto"):
+                ours.update(self._parse(os.path.join(self.OURS, name)))
+        with open(os.path.join(GOLDEN, "proto_fields.json")) as f:
+            ref = {
+                msg: {fname: num for fname, num, _ in fields}
+                for msg, fields in json.load(f)["messages"].items()
+            }
         shared = set(ours) & set(ref)
         # every reference message must exist in ours
         assert set(ref) - {"Empty", "JobState"} <= set(ours), (
