@@ -20,6 +20,7 @@ setup(
             name="shockwave_amd.ops._C",
             sources=[
                 "shockwave_amd/ops/csrc/fused_ops.hip",
+                "shockwave_amd/ops/csrc/capturable_ops.hip",
                 "shockwave_amd/ops/csrc/bindings.cpp",
             ],
             extra_compile_args={

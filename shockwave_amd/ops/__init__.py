@@ -152,3 +152,144 @@ def gns_window_stats(
         return out[0], out[1]
     mean = torch.stack(window_grads).mean(dim=0)
     return (mean * mean).sum(), (window_grads[-1] * window_grads[-1]).sum()
+
+
+# ---------------------------------------------------------------------------
+# capturable (graph-safe) optimizer steps: scalars in device memory
+# ---------------------------------------------------------------------------
+#
+# Scalar block: one contiguous fp32 tensor per optimizer, 32-bit words
+#   [0] grad_norm  [1] clip_coef  [2] step (int32 bits)  [3] reserved
+#   [4+g] lr of param group g
+# (layout shared with csrc/capturable_ops.hip).
+
+CHUNK_ELEMS = 32768
+SCALAR_GRAD_NORM = 0
+SCALAR_CLIP_COEF = 1
+SCALAR_STEP = 2
+SCALAR_LR0 = 4
+
+
+def num_chunks(tensors: List[torch.Tensor]) -> int:
+    """Blocks (= partial sums) the multi-tensor kernels use for a list."""
+    return sum((t.numel() + CHUNK_ELEMS - 1) // CHUNK_ELEMS for t in tensors)
+
+
+def new_scalar_block(num_groups: int, device) -> torch.Tensor:
+    """Zeroed scalar block (step 0, clip_coef 1) for ``num_groups`` lrs."""
+    block = torch.zeros(SCALAR_LR0 + num_groups, dtype=torch.float32,
+                        device=device)
+    block[SCALAR_CLIP_COEF] = 1.0
+    return block
+
+
+def scalar_step_view(scalars: torch.Tensor) -> torch.Tensor:
+    """int32 view (shape [1]) of the step word of a scalar block."""
+    return scalars.view(torch.int32)[SCALAR_STEP:SCALAR_STEP + 1]
+
+
+def multi_tensor_sumsq_partials(
+    tensors: List[torch.Tensor], partials: torch.Tensor, offset: int = 0
+) -> int:
+    """partials[offset + b] = sum of squares of chunk b of ``tensors``
+    (32K-element chunks, tensor-major).  Returns the chunk count."""
+    if tensors[0].is_cuda:
+        _require_ext()
+        return _C.multi_tensor_sumsq_partials(tensors, partials, offset)
+    b = offset
+    for t in tensors:
+        flat = t.reshape(-1)
+        for c in range(0, flat.numel(), CHUNK_ELEMS):
+            chunk = flat[c:c + CHUNK_ELEMS]
+            partials[b] = (chunk * chunk).sum()
+            b += 1
+    assert b <= partials.numel(), "partials workspace too small"
+    return b - offset
+
+
+def optim_prologue(
+    partials: torch.Tensor,
+    num_partials: int,
+    scalars: torch.Tensor,
+    max_norm: float = 0.0,
+    clip: bool = False,
+) -> None:
+    """Start one optimizer step: grad_norm = sqrt(sum(partials[:n])),
+    clip_coef = min(1, max_norm / (grad_norm + 1e-6)) (1 when ``clip`` is
+    off), step += 1 — all written into ``scalars`` on its device."""
+    if scalars.is_cuda:
+        _require_ext()
+        _C.optim_prologue(partials, num_partials, scalars, max_norm, clip)
+        return
+    norm = partials[:num_partials].sum().sqrt()
+    scalars[SCALAR_GRAD_NORM] = norm
+    if clip:
+        scalars[SCALAR_CLIP_COEF] = torch.clamp(
+            max_norm / (norm + 1e-6), max=1.0
+        )
+    else:
+        scalars[SCALAR_CLIP_COEF] = 1.0
+    scalar_step_view(scalars).add_(1)
+
+
+def fused_sgd_cap(
+    params: List[torch.Tensor],
+    grads: List[torch.Tensor],
+    momentum_bufs: List[torch.Tensor],
+    scalars: torch.Tensor,
+    group: int = 0,
+    momentum: float = 0.0,
+    dampening: float = 0.0,
+    weight_decay: float = 0.0,
+    nesterov: bool = False,
+) -> None:
+    """``fused_sgd`` with lr, the first-step flag (step == 1 after the
+    prologue's advance) and clip_coef read from ``scalars``.  The gradient
+    is scaled by clip_coef on the fly; ``grads`` are not modified."""
+    if params[0].is_cuda:
+        _require_ext()
+        _C.fused_sgd_cap(
+            params, grads, momentum_bufs, scalars, group, momentum,
+            dampening, weight_decay, nesterov,
+        )
+        return
+    coef = scalars[SCALAR_CLIP_COEF]
+    step = int(scalar_step_view(scalars).item())
+    fused_sgd(
+        params, [g * coef for g in grads], momentum_bufs,
+        lr=float(scalars[SCALAR_LR0 + group]), momentum=momentum,
+        dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
+        buf_initialized=(step - 1) != 0,
+    )
+
+
+def fused_adam_cap(
+    params: List[torch.Tensor],
+    grads: List[torch.Tensor],
+    exp_avgs: List[torch.Tensor],
+    exp_avg_sqs: List[torch.Tensor],
+    scalars: torch.Tensor,
+    group: int = 0,
+    beta1: float = 0.9,
+    beta2: float = 0.999,
+    eps: float = 1e-8,
+    weight_decay: float = 0.0,
+    adamw: bool = False,
+) -> None:
+    """``fused_adam`` with lr, step and clip_coef read from ``scalars``.
+    The gradient is scaled by clip_coef on the fly; ``grads`` are not
+    modified."""
+    if params[0].is_cuda:
+        _require_ext()
+        _C.fused_adam_cap(
+            params, grads, exp_avgs, exp_avg_sqs, scalars, group, beta1,
+            beta2, eps, weight_decay, adamw,
+        )
+        return
+    coef = scalars[SCALAR_CLIP_COEF]
+    fused_adam(
+        params, [g * coef for g in grads], exp_avgs, exp_avg_sqs,
+        lr=float(scalars[SCALAR_LR0 + group]), beta1=beta1, beta2=beta2,
+        eps=eps, weight_decay=weight_decay,
+        step=int(scalar_step_view(scalars).item()), adamw=adamw,
+    )

@@ -1,4 +1,5 @@
-// Torch glue for the CDNA4 fused multi-tensor kernels (fused_ops.hip).
+// Torch glue for the CDNA4 fused multi-tensor kernels (fused_ops.hip,
+// capturable_ops.hip).
 //
 // Responsibilities:
 //   * validate tensor lists (fp32, contiguous, same device)
@@ -25,11 +26,19 @@ void swq_launch_multi_tensor_l2norm_sq(const long long*, int, int, float*,
                                        void*);
 void swq_launch_gns_window_stats(const long long*, int, long long, float*,
                                  void*);
+void swq_launch_multi_tensor_sumsq_partials(const long long*, int, int,
+                                            float*, void*);
+void swq_launch_optim_prologue(const float*, int, float*, float, int, void*);
+void swq_launch_fused_sgd_cap(const long long*, int, int, const float*, int,
+                              float, float, float, int, void*);
+void swq_launch_fused_adam_cap(const long long*, int, int, const float*, int,
+                               float, float, float, float, int, void*);
 }
 
 namespace {
 
-constexpr long long kChunkElems = 32768;  // keep in sync with fused_ops.hip
+constexpr long long kChunkElems = 32768;  // keep in sync with swq_common.h
+constexpr int kScalarLr0 = 4;  // keep in sync with capturable_ops.hip
 
 struct MetaEntry {
     torch::Tensor device_buf;
@@ -205,6 +214,96 @@ torch::Tensor gns_window_stats(std::vector<torch::Tensor> grads,
     return out;
 }
 
+// ---------------------------------------------------------------------------
+// capturable optimizers (capturable_ops.hip): scalars live in `scalars`, a
+// device fp32 block owned by the optimizer (layout in capturable_ops.hip)
+// ---------------------------------------------------------------------------
+
+namespace {
+
+void check_scalars(const torch::Tensor& scalars, int64_t group,
+                   const torch::Tensor& ref) {
+    TORCH_CHECK(scalars.is_cuda() && scalars.device() == ref.device(),
+                "scalar block must live on the params' device");
+    TORCH_CHECK(scalars.scalar_type() == torch::kFloat32 &&
+                    scalars.is_contiguous(),
+                "scalar block must be contiguous fp32");
+    TORCH_CHECK(group >= 0 && scalars.numel() > kScalarLr0 + group,
+                "scalar block too small for param group ", group);
+}
+
+}  // namespace
+
+int64_t multi_tensor_sumsq_partials(std::vector<torch::Tensor> tensors,
+                                    torch::Tensor partials, int64_t offset) {
+    std::vector<std::vector<torch::Tensor>> lists{tensors};
+    check_lists(lists);
+    const auto& meta = get_meta(lists);
+    TORCH_CHECK(partials.is_cuda() &&
+                    partials.device() == tensors[0].device() &&
+                    partials.scalar_type() == torch::kFloat32 &&
+                    partials.is_contiguous(),
+                "partials must be a contiguous fp32 device tensor");
+    TORCH_CHECK(offset >= 0 && offset + meta.num_chunks <= partials.numel(),
+                "partials workspace too small: need ",
+                offset + meta.num_chunks, ", have ", partials.numel());
+    swq_launch_multi_tensor_sumsq_partials(
+        (const long long*)meta.device_buf.data_ptr<int64_t>(),
+        (int)tensors.size(), meta.num_chunks,
+        partials.data_ptr<float>() + offset, current_stream(tensors[0]));
+    return meta.num_chunks;
+}
+
+void optim_prologue(torch::Tensor partials, int64_t num_partials,
+                    torch::Tensor scalars, double max_norm, bool clip) {
+    check_scalars(scalars, 0, scalars);
+    TORCH_CHECK(partials.is_cuda() &&
+                    partials.device() == scalars.device() &&
+                    partials.scalar_type() == torch::kFloat32 &&
+                    partials.is_contiguous(),
+                "partials must be a contiguous fp32 device tensor");
+    TORCH_CHECK(num_partials >= 0 && num_partials <= partials.numel(),
+                "num_partials out of range");
+    swq_launch_optim_prologue(partials.data_ptr<float>(), (int)num_partials,
+                              scalars.data_ptr<float>(), (float)max_norm,
+                              clip ? 1 : 0, current_stream(scalars));
+}
+
+void fused_sgd_cap(std::vector<torch::Tensor> params,
+                   std::vector<torch::Tensor> grads,
+                   std::vector<torch::Tensor> momentum_bufs,
+                   torch::Tensor scalars, int64_t group, double momentum,
+                   double dampening, double weight_decay, bool nesterov) {
+    std::vector<std::vector<torch::Tensor>> lists{params, grads, momentum_bufs};
+    check_lists(lists);
+    check_scalars(scalars, group, params[0]);
+    const auto& meta = get_meta(lists);
+    swq_launch_fused_sgd_cap(
+        (const long long*)meta.device_buf.data_ptr<int64_t>(),
+        (int)params.size(), meta.num_chunks, scalars.data_ptr<float>(),
+        (int)group, (float)momentum, (float)dampening, (float)weight_decay,
+        nesterov ? 1 : 0, current_stream(params[0]));
+}
+
+void fused_adam_cap(std::vector<torch::Tensor> params,
+                    std::vector<torch::Tensor> grads,
+                    std::vector<torch::Tensor> exp_avgs,
+                    std::vector<torch::Tensor> exp_avg_sqs,
+                    torch::Tensor scalars, int64_t group, double beta1,
+                    double beta2, double eps, double weight_decay,
+                    bool adamw) {
+    std::vector<std::vector<torch::Tensor>> lists{params, grads, exp_avgs,
+                                                  exp_avg_sqs};
+    check_lists(lists);
+    check_scalars(scalars, group, params[0]);
+    const auto& meta = get_meta(lists);
+    swq_launch_fused_adam_cap(
+        (const long long*)meta.device_buf.data_ptr<int64_t>(),
+        (int)params.size(), meta.num_chunks, scalars.data_ptr<float>(),
+        (int)group, (float)beta1, (float)beta2, (float)eps,
+        (float)weight_decay, adamw ? 1 : 0, current_stream(params[0]));
+}
+
 void clear_meta_cache() { g_meta_cache.clear(); }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -216,5 +315,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "per-tensor squared L2 norms");
     m.def("gns_window_stats", &gns_window_stats,
           "window-average + current grad squared norms");
+    m.def("multi_tensor_sumsq_partials", &multi_tensor_sumsq_partials,
+          "per-chunk sum of squares into partials[offset:]; returns chunks");
+    m.def("optim_prologue", &optim_prologue,
+          "global norm + clip coefficient + step advance (one block)");
+    m.def("fused_sgd_cap", &fused_sgd_cap,
+          "fused SGD step with device-side lr / step / clip");
+    m.def("fused_adam_cap", &fused_adam_cap,
+          "fused Adam/AdamW step with device-side lr / step / clip");
     m.def("clear_meta_cache", &clear_meta_cache);
 }

@@ -9,13 +9,37 @@ pre-created with the param's layout and never set to None (see
 ``_preinit_grads`` and workloads.common.zero_grads), so the param/grad/
 state tensor identities are stable across steps — the cache removes
 ~100 us of per-step Python when the GPU step itself is ~2 ms.
+
+Capturable mode (``capturable=True`` or ``max_grad_norm=...``): lr, the
+step counter and the clip coefficient live in a device-resident scalar
+block that the kernels read, so one captured hipGraph of ``step()`` stays
+correct across steps, LR changes and session reuse.  With
+``max_grad_norm`` the global L2 norm over ALL param groups is reduced on
+device (deterministically, no atomics) and the clip is applied to the
+gradient in registers inside the update kernel.  Unlike
+``torch.nn.utils.clip_grad_norm_`` this does NOT modify ``.grad``: code
+that reads gradients after ``step()`` (Accordion, GNS) keeps seeing the
+raw values.  With both options at their defaults the by-value kernels run
+exactly as before.
 """
 
 from __future__ import annotations
 
 import torch
 
-from . import fused_adam, fused_sgd
+from . import (
+    SCALAR_GRAD_NORM,
+    SCALAR_LR0,
+    fused_adam,
+    fused_adam_cap,
+    fused_sgd,
+    fused_sgd_cap,
+    multi_tensor_sumsq_partials,
+    new_scalar_block,
+    num_chunks,
+    optim_prologue,
+    scalar_step_view,
+)
 
 
 def _load_state_inplace(opt, state_dict, tensor_keys):
@@ -63,6 +87,9 @@ def reset_optimizer_state_inplace(opt):
         opt._step_count = 0
     if isinstance(opt, FusedSGD):
         opt._buffers_initialized = False
+    if getattr(opt, "capturable", False) and opt._scalars is not None:
+        # the device step is what a captured graph reads
+        scalar_step_view(opt._scalars).zero_()
 
 
 def _preinit_grads(param_groups):
@@ -78,15 +105,111 @@ def _preinit_grads(param_groups):
                 p.grad = torch.zeros_like(p)
 
 
-class FusedSGD(torch.optim.Optimizer):
+class _CapturableMixin:
+    """Device-resident lr / step / clip state shared by the fused
+    optimizers.  Subclasses provide ``_build_lists`` (entries start with
+    ``(group, params, grads, ...)``) and ``_cached_lists``."""
+
+    def _init_capturable(self, max_grad_norm, capturable):
+        self.max_grad_norm = max_grad_norm
+        self.capturable = bool(capturable) or max_grad_norm is not None
+        self._scalars = None    # scalar block, see ops/__init__.py
+        self._partials = None   # per-chunk sum-of-squares workspace
+        self._pushed_lr = None  # host mirror of the device lrs
+
+    def _ensure_lists(self):
+        """Build (once) the tensor lists and, in capturable mode, the
+        scalar block and partials workspace cached with them.  Both keep
+        their addresses when the lists are rebuilt."""
+        if self._cached_lists is None:
+            self._cached_lists = self._build_lists()
+        if not self.capturable:
+            return
+        if self._scalars is None:
+            device = self.param_groups[0]["params"][0].device
+            self._scalars = new_scalar_block(len(self.param_groups), device)
+            self._pushed_lr = [None] * len(self.param_groups)
+        chunks = sum(num_chunks(entry[2]) for entry in self._cached_lists)
+        if self._partials is None or self._partials.numel() < max(1, chunks):
+            self._partials = torch.zeros(
+                max(1, chunks), dtype=torch.float32,
+                device=self._scalars.device,
+            )
+
+    def _begin_capturable_step(self):
+        """Norm partials (when clipping) + the one-block prologue."""
+        if not _stream_is_capturing():
+            self.sync_hyperparams()
+        n = 0
+        clip = self.max_grad_norm is not None
+        if clip:
+            for entry in self._cached_lists:
+                if entry[1]:
+                    n += multi_tensor_sumsq_partials(
+                        entry[2], self._partials, n
+                    )
+        optim_prologue(
+            self._partials, n, self._scalars,
+            max_norm=float(self.max_grad_norm) if clip else 0.0, clip=clip,
+        )
+
+    def set_lr(self, value, group=None):
+        """Set the learning rate of one param group (all when ``group`` is
+        None).  In capturable mode the device scalar is written in place,
+        so a captured graph picks the new value up on its next replay."""
+        groups = range(len(self.param_groups)) if group is None else [group]
+        for gi in groups:
+            self.param_groups[gi]["lr"] = value
+        self.sync_hyperparams()
+
+    def sync_hyperparams(self):
+        """Push any ``param_groups[i]['lr']`` that changed on the host
+        (e.g. through a torch LR scheduler) to the device scalars.  No-op
+        when nothing changed.  Call it outside a graph capture."""
+        if not self.capturable:
+            return
+        self._ensure_lists()
+        for gi, group in enumerate(self.param_groups):
+            lr = float(group["lr"])
+            if self._pushed_lr[gi] != lr:
+                self._scalars[SCALAR_LR0 + gi].fill_(lr)
+                self._pushed_lr[gi] = lr
+
+    @property
+    def grad_norm(self):
+        """0-dim device tensor: global pre-clip gradient L2 norm of the
+        last step (a view of the scalar block; no host sync).  Computed
+        only when ``max_grad_norm`` is set, else 0."""
+        if not self.capturable:
+            raise RuntimeError("grad_norm requires a capturable optimizer")
+        self._ensure_lists()
+        return self._scalars[SCALAR_GRAD_NORM]
+
+    def _device_step(self):
+        return int(scalar_step_view(self._scalars).item())
+
+    def _set_device_step(self, value):
+        self._ensure_lists()
+        scalar_step_view(self._scalars).fill_(int(value))
+        # a checkpoint's param_groups may carry a different lr
+        self.sync_hyperparams()
+
+
+def _stream_is_capturing():
+    return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+
+
+class FusedSGD(_CapturableMixin, torch.optim.Optimizer):
     def __init__(self, params, lr, momentum=0.0, dampening=0.0,
-                 weight_decay=0.0, nesterov=False):
+                 weight_decay=0.0, nesterov=False, max_grad_norm=None,
+                 capturable=False):
         defaults = dict(lr=lr, momentum=momentum, dampening=dampening,
                         weight_decay=weight_decay, nesterov=nesterov)
         super().__init__(params, defaults)
         _preinit_grads(self.param_groups)
         self._cached_lists = None
         self._buffers_initialized = False
+        self._init_capturable(max_grad_norm, capturable)
 
     def _build_lists(self):
         cached = []
@@ -110,8 +233,22 @@ class FusedSGD(torch.optim.Optimizer):
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
-        if self._cached_lists is None:
-            self._cached_lists = self._build_lists()
+        self._ensure_lists()
+        if self.capturable:
+            self._begin_capturable_step()
+            for gi, (group, params, grads, bufs) in enumerate(
+                self._cached_lists
+            ):
+                if not params:
+                    continue
+                fused_sgd_cap(
+                    params, grads, bufs, self._scalars, gi,
+                    momentum=group["momentum"],
+                    dampening=group["dampening"],
+                    weight_decay=group["weight_decay"],
+                    nesterov=group["nesterov"],
+                )
+            return loss
         buf_initialized = self._buffers_initialized
         self._buffers_initialized = True
         for group, params, grads, bufs in self._cached_lists:
@@ -127,25 +264,45 @@ class FusedSGD(torch.optim.Optimizer):
             )
         return loss
 
+    def state_dict(self):
+        d = super().state_dict()
+        if self.capturable:
+            self._ensure_lists()
+            d["swq_step_count"] = self._device_step()
+        return d
+
     def load_state_dict(self, state_dict):
+        saved_step = state_dict.get("swq_step_count")
+        state_dict = {k: v for k, v in state_dict.items()
+                      if k != "swq_step_count"}
+        if self.capturable:
+            self._ensure_lists()  # state tensors exist: load in place
         if _load_state_inplace(self, state_dict, ("momentum_buffer",)):
             # addresses unchanged: cached lists (and any captured graph)
             # stay valid
             self._buffers_initialized = any(
                 "momentum_buffer" in s for s in self.state.values()
             )
-            return
-        super().load_state_dict(state_dict)
-        self._cached_lists = None  # state tensors were replaced
-        # restored momentum buffers must accumulate, not be overwritten
-        self._buffers_initialized = any(
-            "momentum_buffer" in s for s in self.state.values()
-        )
+        else:
+            super().load_state_dict(state_dict)
+            self._cached_lists = None  # state tensors were replaced
+            # restored momentum buffers must accumulate, not be overwritten
+            self._buffers_initialized = any(
+                "momentum_buffer" in s for s in self.state.values()
+            )
+        if self.capturable:
+            # into the existing device word; a checkpoint without a step
+            # (stock SGD, non-capturable FusedSGD) resumes past the
+            # first-step branch iff it carries momentum buffers
+            if saved_step is None:
+                saved_step = 1 if self._buffers_initialized else 0
+            self._set_device_step(saved_step)
 
 
-class FusedAdam(torch.optim.Optimizer):
+class FusedAdam(_CapturableMixin, torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
-                 weight_decay=0.0, adamw=False, amsgrad=False):
+                 weight_decay=0.0, adamw=False, amsgrad=False,
+                 max_grad_norm=None, capturable=False):
         assert not amsgrad, "amsgrad not supported by the fused kernel"
         defaults = dict(lr=lr, betas=betas, eps=eps,
                         weight_decay=weight_decay, adamw=adamw)
@@ -153,6 +310,7 @@ class FusedAdam(torch.optim.Optimizer):
         _preinit_grads(self.param_groups)
         self._cached_lists = None
         self._step_count = 0
+        self._init_capturable(max_grad_norm, capturable)
 
     def _build_lists(self):
         cached = []
@@ -175,8 +333,22 @@ class FusedAdam(torch.optim.Optimizer):
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
-        if self._cached_lists is None:
-            self._cached_lists = self._build_lists()
+        self._ensure_lists()
+        if self.capturable:
+            self._begin_capturable_step()
+            for gi, (group, params, grads, avgs, sqs) in enumerate(
+                self._cached_lists
+            ):
+                if not params:
+                    continue
+                beta1, beta2 = group["betas"]
+                fused_adam_cap(
+                    params, grads, avgs, sqs, self._scalars, gi,
+                    beta1=beta1, beta2=beta2, eps=group["eps"],
+                    weight_decay=group["weight_decay"],
+                    adamw=group["adamw"],
+                )
+            return loss
         self._step_count += 1
         for group, params, grads, avgs, sqs in self._cached_lists:
             if not params:
@@ -192,6 +364,9 @@ class FusedAdam(torch.optim.Optimizer):
 
     def state_dict(self):
         d = super().state_dict()
+        if self.capturable:
+            self._ensure_lists()
+            self._step_count = self._device_step()
         d["swq_step_count"] = self._step_count
         return d
 
@@ -210,6 +385,10 @@ class FusedAdam(torch.optim.Optimizer):
                 for s in state_dict.get("state", {}).values()
             ]
             self._step_count = max(steps) if steps else 0
+        if self.capturable:
+            # into the existing device word: a captured graph keeps reading
+            # the same address
+            self._set_device_step(self._step_count)
         # drop a stock-Adam 'step' scalar so the in-place path does not
         # stash it; our step count is _step_count
         slim = {
@@ -220,12 +399,15 @@ class FusedAdam(torch.optim.Optimizer):
             },
         }
         if _load_state_inplace(self, slim, ("exp_avg", "exp_avg_sq")):
+            self.sync_hyperparams()
             return
         super().load_state_dict(state_dict)
         self._cached_lists = None
+        self.sync_hyperparams()
 
 
 class FusedAdamW(FusedAdam):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
-                 weight_decay=1e-2):
-        super().__init__(params, lr, betas, eps, weight_decay, adamw=True)
+                 weight_decay=1e-2, max_grad_norm=None, capturable=False):
+        super().__init__(params, lr, betas, eps, weight_decay, adamw=True,
+                         max_grad_norm=max_grad_norm, capturable=capturable)

@@ -11,9 +11,15 @@ Works because the rest of the stack keeps addresses stable:
 * the fused optimizer's tensor metadata is cached on device,
 * DDP gradients live in persistent flat bucket buffers.
 
-Scalars captured in the graph (e.g. the learning rate passed to the fused
-kernel) are frozen; call ``recapture()`` after changing them (the
-workloads' epoch-level LR schedules re-capture at epoch boundaries).
+Scalars passed to a kernel by value (e.g. the learning rate of the default
+fused optimizers) are frozen in the graph.  The workloads do NOT re-capture:
+the training loop replays a session's graph only while the lr still equals
+the one at capture and otherwise runs eager (workloads/loop.py,
+``can_reuse_graph``); ``recapture()`` exists for callers that want a fresh
+graph instead.  Capturable optimizers (``FusedSGD/FusedAdam(capturable=True)``
+or ``max_grad_norm=...``, ops/optim.py) keep lr, step count and clip
+coefficient in device memory, so their graph stays correct across steps and
+LR changes with no re-capture.
 """
 
 from __future__ import annotations

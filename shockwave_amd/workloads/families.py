@@ -152,6 +152,17 @@ def imagenet_main(argv=None, mode=None, client=None, max_steps_override=None):
 # translation (Transformer)
 # ---------------------------------------------------------------------------
 
+TRANSFORMER_D_MODEL = 512  # TranslationTransformer default width
+
+
+def transformer_warmup_lr(d_model, n_warmup_steps, step):
+    """Transformer warm-up (reference translation/transformer/Optim.py):
+    d_model^-0.5 * min(step^-0.5, step * n_warmup_steps^-1.5), step >= 1."""
+    return d_model ** -0.5 * min(
+        step ** -0.5, step * n_warmup_steps ** -1.5
+    )
+
+
 def translation_main(argv=None, mode=None, client=None,
                      max_steps_override=None):
     p = argparse.ArgumentParser()
@@ -159,8 +170,12 @@ def translation_main(argv=None, mode=None, client=None,
     p.add_argument("-batch_size", type=int, default=64)
     p.add_argument("-proj_share_weight", action="store_true")
     p.add_argument("-lr", type=float, default=1e-4)
+    p.add_argument("-n_warmup_steps", type=int, default=0,
+                   help="0 = fixed -lr; N > 0 = the reference's warm-up "
+                        "schedule d_model^-0.5 * min(n^-0.5, n * N^-1.5)")
     common.add_scheduler_args(p, "-step")
     args = p.parse_args(argv)
+    warmup = args.n_warmup_steps > 0
 
     criterion = nn.CrossEntropyLoss(ignore_index=0)
 
@@ -182,11 +197,17 @@ def translation_main(argv=None, mode=None, client=None,
             synthetic.SyntheticTranslation(10000), a, a.batch_size
         ),
         build_optimizer=lambda a, params: FusedAdam(
-            params, lr=a.lr, betas=(0.9, 0.98), eps=1e-9
+            params, lr=a.lr, betas=(0.9, 0.98), eps=1e-9,
+            capturable=warmup,
         ),
         step=step,
         supports_accordion=False,   # scheduler rule: no Accordion on
         supports_gns=True,          # transformers (scheduler.py:1670-1672)
+        lr_schedule=(
+            (lambda a, n: transformer_warmup_lr(
+                TRANSFORMER_D_MODEL, a.n_warmup_steps, n))
+            if warmup else None
+        ),
     )
     return run(spec, args, mode=mode, client=client,
                max_steps_override=max_steps_override)
@@ -223,6 +244,10 @@ def lm_main(argv=None, mode=None, client=None, max_steps_override=None):
     p.add_argument("--batch_size", type=int, default=20)
     p.add_argument("--lr", type=float, default=20.0)
     p.add_argument("--clip", type=float, default=0.25)
+    p.add_argument("--apply_clip", action="store_true",
+                   help="train at the full --lr with the global gradient "
+                        "norm clipped to --clip inside the fused step "
+                        "(the reference recipe) instead of at lr/20")
     common.add_scheduler_args(p, "--steps")
     args = p.parse_args(argv)
 
@@ -246,7 +271,10 @@ def lm_main(argv=None, mode=None, client=None, max_steps_override=None):
         build_loader=lambda a: _CorpusLoader(
             synthetic.SyntheticCorpus(), a.batch_size
         ),
-        build_optimizer=lambda a, params: FusedSGD(params, lr=a.lr / 20.0),
+        build_optimizer=lambda a, params: (
+            FusedSGD(params, lr=a.lr, max_grad_norm=a.clip)
+            if a.apply_clip else FusedSGD(params, lr=a.lr / 20.0)
+        ),
         step=step,
     )
     return run(spec, args, mode=mode, client=client,

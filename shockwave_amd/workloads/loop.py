@@ -42,6 +42,24 @@ class WorkloadSpec:
     # launches (shockwave_amd/parallel/graphs.py).
     make_static_batch: Callable = None   # (args, device) -> batch
     copy_batch: Callable = None          # (static_batch, batch) -> None
+    # optional per-step LR schedule, applied through optimizer.set_lr
+    # before each step; ``step`` counts from 1.  A capturable optimizer
+    # (ops/optim.py) takes it without leaving the captured graph.
+    lr_schedule: Callable = None         # (args, step) -> float
+
+
+def can_reuse_graph(sess, optimizer) -> bool:
+    """May this lease replay the hipGraph cached in ``sess``?
+
+    A capturable optimizer reads lr / step from device memory, so its
+    graph stays valid whatever the lr is now.  Any other optimizer has the
+    lr frozen into the captured kernel arguments: reuse only when the
+    current lr equals the one at capture."""
+    if sess.graphed is None:
+        return False
+    if getattr(optimizer, "capturable", False):
+        return True
+    return sess.capture_lr == optimizer.param_groups[0]["lr"]
 
 
 class _Preempted(SystemExit):
@@ -223,7 +241,7 @@ def run(spec: WorkloadSpec, args, mode: Optional[str] = None, client=None,
     ):
         cur_lr = optimizer.param_groups[0]["lr"]
         if sess.graphed is not None:
-            if sess.capture_lr == cur_lr:
+            if can_reuse_graph(sess, optimizer):
                 graphed, static_batch = sess.graphed, sess.static_batch
             # else: lr changed since capture — run eager (scalars are
             # frozen in the graph; see parallel/graphs.py docstring)
@@ -274,13 +292,20 @@ def run(spec: WorkloadSpec, args, mode: Optional[str] = None, client=None,
     except ValueError:
         pass  # not the main thread (in-process tests)
 
+    sync_hyperparams = getattr(optimizer, "sync_hyperparams", None)
     done = False
     try:
         while not done and state["cumulative_steps"] < target_steps:
             hit_target = False
             for batch in trainloader:
+                if spec.lr_schedule is not None:
+                    optimizer.set_lr(spec.lr_schedule(
+                        args, state["cumulative_steps"] + 1
+                    ))
                 if graphed is not None:
                     spec.copy_batch(static_batch, batch)
+                    if sync_hyperparams is not None:
+                        sync_hyperparams()
                     graphed.replay()
                 else:
                     eager_step(batch)
