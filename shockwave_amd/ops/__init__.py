@@ -161,13 +161,31 @@ def gns_window_stats(
 # Scalar block: one contiguous fp32 tensor per optimizer, 32-bit words
 #   [0] grad_norm  [1] clip_coef  [2] step (int32 bits)  [3] reserved
 #   [4+g] lr of param group g
-# (layout shared with csrc/capturable_ops.hip).
+# The kernels take the layout from csrc/swq_layout.h.  The CPU path must
+# work without the extension, so the constants are repeated here and
+# checked against the extension's when it is there.
 
 CHUNK_ELEMS = 32768
 SCALAR_GRAD_NORM = 0
 SCALAR_CLIP_COEF = 1
 SCALAR_STEP = 2
 SCALAR_LR0 = 4
+
+
+def _check_layout(ext) -> None:
+    """Raise unless ``ext`` was compiled with this module's layout."""
+    for name in ("CHUNK_ELEMS", "SCALAR_GRAD_NORM", "SCALAR_CLIP_COEF",
+                 "SCALAR_STEP", "SCALAR_LR0"):
+        if globals()[name] != getattr(ext, name):
+            raise RuntimeError(
+                f"shockwave_amd.ops.{name} = {globals()[name]} but the "
+                f"extension was built with {getattr(ext, name)} "
+                "(csrc/swq_layout.h)"
+            )
+
+
+if HAVE_EXT:
+    _check_layout(_C)
 
 
 def num_chunks(tensors: List[torch.Tensor]) -> int:

@@ -14,12 +14,7 @@
 //                                    clip_coef loaded from the block and
 //                                    the gradient scaled in registers
 //
-// Scalar block layout (32-bit words, one block per optimizer):
-//   [0] float grad_norm   pre-clip global L2 norm (0 when clipping is off)
-//   [1] float clip_coef   min(1, max_norm / (grad_norm + 1e-6)); 1 when off
-//   [2] int   step        optimizer steps taken, counting the one in flight
-//   [3]       reserved
-//   [4+g] float lr of param group g
+// The scalar block's layout is in swq_layout.h.
 //
 // Cross-block hand-off happens only over kernel boundaries on one stream:
 // no block writes a word another block of the same launch reads, and there
@@ -29,35 +24,13 @@
 
 #include "swq_common.h"
 
-#define SWQ_SCALAR_GRAD_NORM 0
-#define SWQ_SCALAR_CLIP_COEF 1
-#define SWQ_SCALAR_STEP 2
-#define SWQ_SCALAR_LR0 4
-
 // ---------------------------------------------------------------------------
 // per-chunk sum of squares.  lists: 0=src.  Plain store, no zeroing needed.
 // ---------------------------------------------------------------------------
 extern "C" __global__ void __launch_bounds__(BLOCK_THREADS)
 swq_multi_tensor_sumsq_partials(const long long* meta, int num_tensors,
                                 float* partials) {
-    MetaView mv{meta, num_tensors, 1};
-    const int t = mv.block_tensor(blockIdx.x);
-    const int c = mv.block_chunk(blockIdx.x);
-    const long long base = (long long)c * CHUNK_ELEMS;
-    const int n = (int)min((long long)CHUNK_ELEMS, mv.numel(t) - base);
-    const float* src = (const float*)mv.addr(0, t) + base;
-
-    float acc = 0.0f;
-    const int vec_n = n / 4;
-    const float4* s4 = (const float4*)src;
-    for (int i = threadIdx.x; i < vec_n; i += BLOCK_THREADS) {
-        float4 s = s4[i];
-        acc += s.x * s.x + s.y * s.y + s.z * s.z + s.w * s.w;
-    }
-    for (int i = vec_n * 4 + threadIdx.x; i < n; i += BLOCK_THREADS)
-        acc += src[i] * src[i];
-
-    const float total = block_reduce_sum(acc);
+    const float total = swq_chunk_sumsq(meta, num_tensors);
     if (threadIdx.x == 0) partials[blockIdx.x] = total;
 }
 
@@ -122,10 +95,8 @@ swq_fused_adam_cap(const long long* meta, int num_tensors,
 }
 
 // ---------------------------------------------------------------------------
-// host-side launchers (torch-independent; called from bindings.cpp).  They
-// allocate nothing and synchronize nothing: the partials workspace and the
-// scalar block are owned by the optimizer.  Grids are one block per chunk,
-// as in fused_ops.hip.
+// host-side launchers (prototypes in swq_layout.h; called from
+// bindings.cpp).  Grids are one block per chunk, as in fused_ops.hip.
 // ---------------------------------------------------------------------------
 extern "C" {
 

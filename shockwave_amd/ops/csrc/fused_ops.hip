@@ -7,13 +7,15 @@
 //   * Accordion grad-accumulate + per-tensor L2 norm (#5)
 //   * GNS window-average + norm estimator        (#6)
 //
-// Design notes (per /opt/skills/guides/cdna_hip_programming.md):
+// Design notes:
 //   * wave = 64 lanes; 256-thread blocks (4 waves per CU workgroup)
-//   * all kernels are HBM-bound: float4 (16 B/lane) vectorized main loops
-//     (guide G13), grid built from 32K-element chunks so even an 11M-param
-//     model yields ~340 workgroups (>256 CUs reachable, G11)
+//   * all kernels are HBM-bound: float4 (16 B/lane) vectorized main loops,
+//     grid built from 32K-element chunks so even an 11M-param model yields
+//     ~340 workgroups (>256 CUs reachable)
+//   * every chunked elementwise kernel is swq_chunk_for_each (swq_common.h)
+//     plus one element functor
 //   * reductions: 64-wide __shfl_down wave reduction -> LDS across the 4
-//     waves -> ONE device-scope atomicAdd per block (G12)
+//     waves -> ONE device-scope atomicAdd per block
 //   * tensor/chunk metadata lives in a cached device buffer (no 4 KiB
 //     kernel-arg limit, graph-capture safe: no allocation at launch time
 //     once the cache is warm)
@@ -54,25 +56,8 @@ swq_fused_adam(const long long* meta, int num_tensors, float lr, float beta1,
 // ---------------------------------------------------------------------------
 extern "C" __global__ void __launch_bounds__(BLOCK_THREADS)
 swq_multi_tensor_accum(const long long* meta, int num_tensors, float alpha) {
-    MetaView mv{meta, num_tensors, 2};
-    const int t = mv.block_tensor(blockIdx.x);
-    const int c = mv.block_chunk(blockIdx.x);
-    const long long base = (long long)c * CHUNK_ELEMS;
-    const int n = (int)min((long long)CHUNK_ELEMS, mv.numel(t) - base);
-    float* dst = (float*)mv.addr(0, t) + base;
-    const float* src = (const float*)mv.addr(1, t) + base;
-
-    const int vec_n = n / 4;
-    float4* d4 = (float4*)dst;
-    const float4* s4 = (const float4*)src;
-    for (int i = threadIdx.x; i < vec_n; i += BLOCK_THREADS) {
-        float4 d = d4[i], s = s4[i];
-        d.x += alpha * s.x; d.y += alpha * s.y;
-        d.z += alpha * s.z; d.w += alpha * s.w;
-        d4[i] = d;
-    }
-    for (int i = vec_n * 4 + threadIdx.x; i < n; i += BLOCK_THREADS)
-        dst[i] += alpha * src[i];
+    swq_chunk_for_each<2>(meta, num_tensors, 0b01u,
+                          [=](auto& e) { e[0] += alpha * e[1]; });
 }
 
 // ---------------------------------------------------------------------------
@@ -82,24 +67,8 @@ swq_multi_tensor_accum(const long long* meta, int num_tensors, float alpha) {
 extern "C" __global__ void __launch_bounds__(BLOCK_THREADS)
 swq_multi_tensor_l2norm_sq(const long long* meta, int num_tensors,
                            float* out) {
-    MetaView mv{meta, num_tensors, 1};
-    const int t = mv.block_tensor(blockIdx.x);
-    const int c = mv.block_chunk(blockIdx.x);
-    const long long base = (long long)c * CHUNK_ELEMS;
-    const int n = (int)min((long long)CHUNK_ELEMS, mv.numel(t) - base);
-    const float* src = (const float*)mv.addr(0, t) + base;
-
-    float acc = 0.0f;
-    const int vec_n = n / 4;
-    const float4* s4 = (const float4*)src;
-    for (int i = threadIdx.x; i < vec_n; i += BLOCK_THREADS) {
-        float4 s = s4[i];
-        acc += s.x * s.x + s.y * s.y + s.z * s.z + s.w * s.w;
-    }
-    for (int i = vec_n * 4 + threadIdx.x; i < n; i += BLOCK_THREADS)
-        acc += src[i] * src[i];
-
-    const float total = block_reduce_sum(acc);
+    int t;
+    const float total = swq_chunk_sumsq(meta, num_tensors, &t);
     if (threadIdx.x == 0) atomicAdd(&out[t], total);
 }
 
@@ -111,9 +80,9 @@ swq_multi_tensor_l2norm_sq(const long long* meta, int num_tensors,
 //   out[0] += || (1/W) sum_w g_w ||^2    (big-batch norm estimate)
 //   out[1] += || g_{W-1} ||^2            (small-batch norm)
 // Zero out[0:2] before launch.  Grid-stride, one pass over all W grads
-// (W <= 8: per-lane accumulation in registers, 16 B loads per grad).
+// (any W: the window is a runtime loop, per-lane accumulation in registers,
+// 16 B loads per grad).  Not chunked: one flat buffer per gradient.
 // ---------------------------------------------------------------------------
-#define GNS_MAX_WINDOW 16
 extern "C" __global__ void __launch_bounds__(BLOCK_THREADS)
 swq_gns_window_stats(const long long* grad_ptrs, int window, long long n,
                      float* out) {
@@ -159,7 +128,7 @@ swq_gns_window_stats(const long long* grad_ptrs, int window, long long n,
 }
 
 // ---------------------------------------------------------------------------
-// host-side launchers (torch-independent; called from bindings.cpp)
+// host-side launchers (prototypes in swq_layout.h; called from bindings.cpp)
 // ---------------------------------------------------------------------------
 extern "C" {
 
@@ -200,7 +169,7 @@ void swq_launch_gns_window_stats(const long long* grad_ptrs, int window,
                                  long long n, float* out, void* stream) {
     long long vec_n = n / 4;
     int blocks = (int)((vec_n + BLOCK_THREADS - 1) / BLOCK_THREADS);
-    if (blocks > 2048) blocks = 2048;  // grid-stride past this (guide G11)
+    if (blocks > 2048) blocks = 2048;  // grid-stride past this
     if (blocks < 1) blocks = 1;
     hipLaunchKernelGGL(swq_gns_window_stats, dim3(blocks),
                        dim3(BLOCK_THREADS), 0, (hipStream_t)stream, grad_ptrs,

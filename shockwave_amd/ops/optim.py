@@ -42,7 +42,7 @@ from . import (
 )
 
 
-def _load_state_inplace(opt, state_dict, tensor_keys):
+def _load_state_inplace(opt, state_dict):
     """Copy a checkpoint's per-param state tensors INTO the optimizer's
     existing state tensors (same addresses) instead of replacing them —
     a session-cached hipGraph holds the old addresses.  Returns False on
@@ -105,17 +105,43 @@ def _preinit_grads(param_groups):
                 p.grad = torch.zeros_like(p)
 
 
-class _CapturableMixin:
-    """Device-resident lr / step / clip state shared by the fused
-    optimizers.  Subclasses provide ``_build_lists`` (entries start with
-    ``(group, params, grads, ...)``) and ``_cached_lists``."""
+class _FusedOptimizer(torch.optim.Optimizer):
+    """The step skeleton and the device-resident lr / step / clip state
+    shared by the fused optimizers.  Subclasses provide
 
-    def _init_capturable(self, max_grad_norm, capturable):
+    * ``_build_lists()``: one ``(group, params, grads, ...)`` entry per
+      param group, the tensor lists in the order their kernel takes them;
+    * ``_advance()``: count one by-value step and return the keyword
+      arguments it adds to every ``_launch``;
+    * ``_launch(group, *lists, **step_kw)``: the by-value kernel;
+    * ``_launch_cap(gi, group, *lists)``: the capturable kernel."""
+
+    def __init__(self, params, defaults, max_grad_norm, capturable):
+        super().__init__(params, defaults)
+        _preinit_grads(self.param_groups)
+        self._cached_lists = None
         self.max_grad_norm = max_grad_norm
         self.capturable = bool(capturable) or max_grad_norm is not None
         self._scalars = None    # scalar block, see ops/__init__.py
         self._partials = None   # per-chunk sum-of-squares workspace
         self._pushed_lr = None  # host mirror of the device lrs
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = closure() if closure is not None else None
+        self._ensure_lists()
+        if self.capturable:
+            self._begin_capturable_step()
+        else:
+            step_kw = self._advance()
+        for gi, (group, *lists) in enumerate(self._cached_lists):
+            if not lists[0]:
+                continue
+            if self.capturable:
+                self._launch_cap(gi, group, *lists)
+            else:
+                self._launch(group, *lists, **step_kw)
+        return loss
 
     def _ensure_lists(self):
         """Build (once) the tensor lists and, in capturable mode, the
@@ -199,17 +225,14 @@ def _stream_is_capturing():
     return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
 
 
-class FusedSGD(_CapturableMixin, torch.optim.Optimizer):
+class FusedSGD(_FusedOptimizer):
     def __init__(self, params, lr, momentum=0.0, dampening=0.0,
                  weight_decay=0.0, nesterov=False, max_grad_norm=None,
                  capturable=False):
         defaults = dict(lr=lr, momentum=momentum, dampening=dampening,
                         weight_decay=weight_decay, nesterov=nesterov)
-        super().__init__(params, defaults)
-        _preinit_grads(self.param_groups)
-        self._cached_lists = None
+        super().__init__(params, defaults, max_grad_norm, capturable)
         self._buffers_initialized = False
-        self._init_capturable(max_grad_norm, capturable)
 
     def _build_lists(self):
         cached = []
@@ -230,39 +253,23 @@ class FusedSGD(_CapturableMixin, torch.optim.Optimizer):
             cached.append((group, params, grads, bufs))
         return cached
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = closure() if closure is not None else None
-        self._ensure_lists()
-        if self.capturable:
-            self._begin_capturable_step()
-            for gi, (group, params, grads, bufs) in enumerate(
-                self._cached_lists
-            ):
-                if not params:
-                    continue
-                fused_sgd_cap(
-                    params, grads, bufs, self._scalars, gi,
-                    momentum=group["momentum"],
-                    dampening=group["dampening"],
-                    weight_decay=group["weight_decay"],
-                    nesterov=group["nesterov"],
-                )
-            return loss
+    def _advance(self):
         buf_initialized = self._buffers_initialized
         self._buffers_initialized = True
-        for group, params, grads, bufs in self._cached_lists:
-            if not params:
-                continue
-            fused_sgd(
-                params, grads, bufs,
-                lr=group["lr"], momentum=group["momentum"],
-                dampening=group["dampening"],
-                weight_decay=group["weight_decay"],
-                nesterov=group["nesterov"],
-                buf_initialized=buf_initialized,
-            )
-        return loss
+        return dict(buf_initialized=buf_initialized)
+
+    @staticmethod
+    def _hyper(group):
+        return {k: group[k] for k in
+                ("momentum", "dampening", "weight_decay", "nesterov")}
+
+    def _launch(self, group, params, grads, bufs, buf_initialized):
+        fused_sgd(params, grads, bufs, lr=group["lr"],
+                  buf_initialized=buf_initialized, **self._hyper(group))
+
+    def _launch_cap(self, gi, group, params, grads, bufs):
+        fused_sgd_cap(params, grads, bufs, self._scalars, gi,
+                      **self._hyper(group))
 
     def state_dict(self):
         d = super().state_dict()
@@ -277,19 +284,15 @@ class FusedSGD(_CapturableMixin, torch.optim.Optimizer):
                       if k != "swq_step_count"}
         if self.capturable:
             self._ensure_lists()  # state tensors exist: load in place
-        if _load_state_inplace(self, state_dict, ("momentum_buffer",)):
-            # addresses unchanged: cached lists (and any captured graph)
-            # stay valid
-            self._buffers_initialized = any(
-                "momentum_buffer" in s for s in self.state.values()
-            )
-        else:
+        # in place, addresses unchanged: cached lists (and any captured
+        # graph) stay valid
+        if not _load_state_inplace(self, state_dict):
             super().load_state_dict(state_dict)
             self._cached_lists = None  # state tensors were replaced
-            # restored momentum buffers must accumulate, not be overwritten
-            self._buffers_initialized = any(
-                "momentum_buffer" in s for s in self.state.values()
-            )
+        # restored momentum buffers must accumulate, not be overwritten
+        self._buffers_initialized = any(
+            "momentum_buffer" in s for s in self.state.values()
+        )
         if self.capturable:
             # into the existing device word; a checkpoint without a step
             # (stock SGD, non-capturable FusedSGD) resumes past the
@@ -299,18 +302,15 @@ class FusedSGD(_CapturableMixin, torch.optim.Optimizer):
             self._set_device_step(saved_step)
 
 
-class FusedAdam(_CapturableMixin, torch.optim.Optimizer):
+class FusedAdam(_FusedOptimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=0.0, adamw=False, amsgrad=False,
                  max_grad_norm=None, capturable=False):
         assert not amsgrad, "amsgrad not supported by the fused kernel"
         defaults = dict(lr=lr, betas=betas, eps=eps,
                         weight_decay=weight_decay, adamw=adamw)
-        super().__init__(params, defaults)
-        _preinit_grads(self.param_groups)
-        self._cached_lists = None
+        super().__init__(params, defaults, max_grad_norm, capturable)
         self._step_count = 0
-        self._init_capturable(max_grad_norm, capturable)
 
     def _build_lists(self):
         cached = []
@@ -330,37 +330,23 @@ class FusedAdam(_CapturableMixin, torch.optim.Optimizer):
             cached.append((group, params, grads, avgs, sqs))
         return cached
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = closure() if closure is not None else None
-        self._ensure_lists()
-        if self.capturable:
-            self._begin_capturable_step()
-            for gi, (group, params, grads, avgs, sqs) in enumerate(
-                self._cached_lists
-            ):
-                if not params:
-                    continue
-                beta1, beta2 = group["betas"]
-                fused_adam_cap(
-                    params, grads, avgs, sqs, self._scalars, gi,
-                    beta1=beta1, beta2=beta2, eps=group["eps"],
-                    weight_decay=group["weight_decay"],
-                    adamw=group["adamw"],
-                )
-            return loss
+    def _advance(self):
         self._step_count += 1
-        for group, params, grads, avgs, sqs in self._cached_lists:
-            if not params:
-                continue
-            beta1, beta2 = group["betas"]
-            fused_adam(
-                params, grads, avgs, sqs,
-                lr=group["lr"], beta1=beta1, beta2=beta2, eps=group["eps"],
-                weight_decay=group["weight_decay"], step=self._step_count,
-                adamw=group["adamw"],
-            )
-        return loss
+        return dict(step=self._step_count)
+
+    @staticmethod
+    def _hyper(group):
+        beta1, beta2 = group["betas"]
+        return dict(beta1=beta1, beta2=beta2, eps=group["eps"],
+                    weight_decay=group["weight_decay"], adamw=group["adamw"])
+
+    def _launch(self, group, params, grads, avgs, sqs, step):
+        fused_adam(params, grads, avgs, sqs, lr=group["lr"], step=step,
+                   **self._hyper(group))
+
+    def _launch_cap(self, gi, group, params, grads, avgs, sqs):
+        fused_adam_cap(params, grads, avgs, sqs, self._scalars, gi,
+                       **self._hyper(group))
 
     def state_dict(self):
         d = super().state_dict()
@@ -398,11 +384,9 @@ class FusedAdam(_CapturableMixin, torch.optim.Optimizer):
                 for k, s in state_dict.get("state", {}).items()
             },
         }
-        if _load_state_inplace(self, slim, ("exp_avg", "exp_avg_sq")):
-            self.sync_hyperparams()
-            return
-        super().load_state_dict(state_dict)
-        self._cached_lists = None
+        if not _load_state_inplace(self, slim):
+            super().load_state_dict(state_dict)
+            self._cached_lists = None
         self.sync_hyperparams()
 
 

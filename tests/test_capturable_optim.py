@@ -313,6 +313,37 @@ def test_gpu_tensors_without_extension_raise(monkeypatch):
 
 
 # ---------------------------------------------------------------------------
+# layout constants: the Python copy against csrc/swq_layout.h
+# ---------------------------------------------------------------------------
+
+LAYOUT_CONSTANTS = ["CHUNK_ELEMS", "SCALAR_GRAD_NORM", "SCALAR_CLIP_COEF",
+                    "SCALAR_STEP", "SCALAR_LR0"]
+
+
+def test_layout_constants_match_the_extension():
+    if not ops.HAVE_EXT:
+        pytest.skip("extension not built")
+    for name in LAYOUT_CONSTANTS:
+        assert getattr(ops._C, name) == getattr(ops, name), name
+
+
+@pytest.mark.parametrize("name", LAYOUT_CONSTANTS)
+def test_layout_check_raises_on_mismatch(monkeypatch, name):
+    ext = types.SimpleNamespace(
+        **{n: getattr(ops, n) for n in LAYOUT_CONSTANTS}
+    )
+    ops._check_layout(ext)  # agreement passes
+    monkeypatch.setattr(ext, name, getattr(ops, name) + 1)
+    with pytest.raises(RuntimeError, match=name):
+        ops._check_layout(ext)
+    # the Python side drifting is caught the same way
+    monkeypatch.undo()
+    monkeypatch.setattr(ops, name, getattr(ops, name) + 1)
+    with pytest.raises(RuntimeError, match=name):
+        ops._check_layout(ext)
+
+
+# ---------------------------------------------------------------------------
 # loop wiring
 # ---------------------------------------------------------------------------
 

@@ -184,6 +184,26 @@ def test_adam_cap_bit_identical_to_fused_adam(adamw, wd):
         torch.testing.assert_close(a, b, rtol=0, atol=0)
 
 
+def test_l2norm_sq_bit_identical_to_sumsq_partials():
+    """The two kernels share one sum-of-squares body.  Tail only, float4
+    loop only (1000 = 250 x 4), float4 loop + tail, exactly one chunk:
+    every tensor is a single chunk, so l2norm's one atomicAdd onto a
+    zeroed word is exact and must equal the plain store of the partials
+    kernel.  Against fp64: a thread adds at most 32 float4 terms, then 8
+    shuffle/LDS levels, so well under 100 roundings of 6e-8 each."""
+    g = torch.Generator().manual_seed(7)
+    sizes = (3, 1000, 1003, 32768)
+    tensors = [torch.randn(s, generator=g).to(DEV) for s in sizes]
+    out = torch.empty(len(tensors), device=DEV)
+    partials = torch.full((len(tensors),), -1.0, device=DEV)
+    ops._C.multi_tensor_l2norm_sq(tensors, out)
+    assert ops.multi_tensor_sumsq_partials(tensors, partials, 0) == len(sizes)
+    torch.cuda.synchronize()
+    assert torch.equal(out, partials)
+    want = torch.stack([(t.double() ** 2).sum() for t in tensors])
+    torch.testing.assert_close(out.double(), want, rtol=1e-5, atol=0)
+
+
 def test_partials_workspace_bounds_are_checked():
     grads = make_grads(0)
     partials = torch.zeros(ops.num_chunks(grads) - 1, device=DEV)
