@@ -230,8 +230,8 @@ def run(spec: WorkloadSpec, args, mode: Optional[str] = None, client=None,
     # capture costs seconds (warmup + MIOpen find on first process); only
     # worth it when this lease will run enough steps to amortize it
     expected_steps = target_steps - state["cumulative_steps"]
-    if lease_it is not None and lease_it._lease.max_steps < 1e9:
-        expected_steps = min(expected_steps, lease_it._lease.max_steps)
+    if lease_it is not None and lease_it.max_steps < 1e9:
+        expected_steps = min(expected_steps, lease_it.max_steps)
     if (
         device.type == "cuda"
         and spec.make_static_batch is not None

@@ -1,11 +1,10 @@
-"""Control-plane tests: RPC loopback, lease iterator protocol, dispatcher."""
+"""Control-plane tests: RPC loopback, dispatcher.  (The lease iterator's
+are in test_lease_iterator.py.)"""
 
-import os
 import threading
 import time
 
 import pytest
-import torch
 
 from shockwave_amd.core.job import JobIdPair
 from shockwave_amd.rpc.services import (
@@ -15,7 +14,6 @@ from shockwave_amd.rpc.services import (
     serve_scheduler,
     serve_worker,
 )
-from shockwave_amd.runtime.lease_iterator import LeaseIterator, NullLeaseClient
 from shockwave_amd.runtime.set_queue import SetQueue
 
 
@@ -139,117 +137,6 @@ class TestWorkerRpcLoopback:
             assert got["reset"] and got["shutdown"]
         finally:
             server.stop(0)
-
-
-class FakeLeaseClient:
-    """Scripted lease behavior for iterator state-machine tests."""
-
-    def __init__(self, leases):
-        self.leases = list(leases)  # [(max_steps, max_duration)]
-        self.init_calls = 0
-        self.update_calls = 0
-        self.rr_calls = []
-
-    def init(self):
-        self.init_calls += 1
-        ms, md = self.leases.pop(0)
-        return ms, md, 0
-
-    def update_lease(self, steps, duration, max_steps, max_duration):
-        self.update_calls += 1
-        if self.leases:
-            ms, md = self.leases.pop(0)
-        else:
-            ms, md = max_steps, max_duration
-        return ms, md, 0, 1e9
-
-    def update_resource_requirement(self, big, small):
-        self.rr_calls.append((big, small))
-
-
-class TestLeaseIterator:
-    def _data(self, n=100):
-        return [(torch.zeros(1), torch.zeros(1)) for _ in range(n)]
-
-    def test_expires_at_max_steps(self, tmp_path):
-        client = FakeLeaseClient([(5, 1e9)])
-        it = LeaseIterator(
-            self._data(), str(tmp_path), lambda: None, lambda s: None,
-            client=client, write_on_close=False,
-        )
-        consumed = list(it)
-        assert len(consumed) == 5
-        assert it.done
-
-    def test_renews_at_75pct(self, tmp_path):
-        client = FakeLeaseClient([(8, 1e9), (16, 1e9)])
-        it = LeaseIterator(
-            self._data(), str(tmp_path), lambda: None, lambda s: None,
-            client=client, write_on_close=False,
-        )
-        consumed = list(it)
-        # renewal granted at 75% of 8 steps -> extended to 16 total
-        assert client.update_calls >= 1
-        assert len(consumed) == 16
-        assert it.done
-
-    def test_infinite_lease_runs_all_data(self, tmp_path):
-        it = LeaseIterator(
-            self._data(30), str(tmp_path), lambda: None, lambda s: None,
-            client=NullLeaseClient(), write_on_close=False,
-        )
-        assert len(list(it)) == 30
-        assert not it.done
-
-    def test_update_resource_requirement_sets_done(self, tmp_path):
-        client = FakeLeaseClient([(100, 1e9)])
-        it = LeaseIterator(
-            self._data(), str(tmp_path), lambda: None, lambda s: None,
-            client=client, write_on_close=False,
-        )
-        it.update_resource_requirement(True, False)
-        assert it.done
-        assert client.rr_calls == [(True, False)]
-
-    def test_deadline_abort(self, tmp_path):
-        class DeadlineClient(FakeLeaseClient):
-            def update_lease(self, steps, duration, max_steps, max_duration):
-                self.update_calls += 1
-                return 1000, 1e9, 1e6, 100  # run_time >> deadline
-
-        client = DeadlineClient([(4, 1e9)])
-        it = LeaseIterator(
-            self._data(), str(tmp_path), lambda: None, lambda s: None,
-            client=client, write_on_close=False,
-        )
-        consumed = list(it)
-        assert it.done  # completed via deadline mechanism
-        assert len(consumed) < 1000
-
-    def test_log_format_scrapeable(self, tmp_path):
-        os.environ["GAVEL_ROUND_ID"] = "3"
-        os.environ["GAVEL_WORKER_ID"] = "1"
-        try:
-            client = FakeLeaseClient([(5, 1e9)])
-            it = LeaseIterator(
-                self._data(), str(tmp_path), lambda: None, lambda s: None,
-                client=client, write_on_close=False,
-            )
-            list(it)
-            it._write_info()
-            it._file_handler.flush()
-            from shockwave_amd.runtime.dispatcher import LOG_LINE_RE
-
-            log_file = tmp_path / ".gavel" / "round=3" / "worker=1.log"
-            steps = None
-            for line in open(log_file):
-                m = LOG_LINE_RE.match(line)
-                if m and m.group("event") == "PROGRESS" and m.group("status") == "STEPS":
-                    steps = int(float(m.group("msg")))
-            assert steps == 5
-        finally:
-            del os.environ["GAVEL_ROUND_ID"]
-            del os.environ["GAVEL_WORKER_ID"]
 
 
 class TestDispatcherProcess:

@@ -88,7 +88,7 @@ class TestLeaseIntegration:
     def test_cifar10_lease_preemption_and_resume(self, tmp_path):
         """Job runs under a finite lease, checkpoints, and resumes with
         preserved step count — the cooperative-preemption contract."""
-        from tests.test_rpc_runtime import FakeLeaseClient
+        from tests.test_lease_iterator import FakeLeaseClient
 
         ckpt_dir = str(tmp_path)
         client = FakeLeaseClient([(4, 1e9)])
@@ -111,7 +111,7 @@ class TestLeaseIntegration:
 
     def test_accordion_requests_rescale(self, tmp_path):
         """Accordion mode leaves the critical regime -> requests big_bs."""
-        from tests.test_rpc_runtime import FakeLeaseClient
+        from tests.test_lease_iterator import FakeLeaseClient
 
         client = FakeLeaseClient([(int(1e9), 1e9)])
         import shockwave_amd.workloads.loop as loop_mod
@@ -138,7 +138,7 @@ class TestGNSLoopIntegration:
     def test_gns_double_requested_when_estimator_fires(self, tmp_path,
                                                        monkeypatch):
         """When GNS says double, the loop reports big_bs and checkpoints."""
-        from tests.test_rpc_runtime import FakeLeaseClient
+        from tests.test_lease_iterator import FakeLeaseClient
         from shockwave_amd.adapt.gns import GNSEstimator
 
         monkeypatch.setattr(GNSEstimator, "should_double",
@@ -166,7 +166,7 @@ class TestAccordionScaleDown:
     def test_reentering_critical_regime_requests_small_bs(self, tmp_path):
         """A job already scaled up (bs 256, original 32) that re-enters the
         critical regime (epochs 150-159 for ResNet-18) reports small_bs."""
-        from tests.test_rpc_runtime import FakeLeaseClient
+        from tests.test_lease_iterator import FakeLeaseClient
         from shockwave_amd.parallel.ckpt_stream import CheckpointStore
         from shockwave_amd.models import resnet18_cifar
         from shockwave_amd.ops.optim import FusedSGD
